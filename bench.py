@@ -13,6 +13,12 @@ chemistry pass.  The total source count is fixed, so --gpus N is STRONG scaling.
 
 metric = cells-traced/s = N^3 x S x K / wall  (BASELINE.json).  Inputs are resident in HBM before the
 timed region.  One JSON line is printed by rank 0.
+
+A plain run only sets up, warms up, times the K steps and prints the line.  --full adds the legs that take runs of
+their own after the timed region (the other sweep mode, the other BASELINE configurations, one GPU's share of eight,
+the drop-in program, the memory-only ceiling, the CPU baseline and the parity check against the oracle); the --no-*
+options switch single legs of --full off.  --dump-outputs DIR writes what the last timed step computed (see
+dump_outputs) for output-by-output comparisons of two builds: the inputs are seeded, the same from run to run.
 """
 import argparse
 import json
@@ -31,6 +37,7 @@ sys.path.insert(0, ROOT)
 HBM_PEAK_GBS = 8000.0            # MI355X_MICROARCH.md: 8 TB/s spec
 SWEEP_BYTES_PER_VISIT = 28       # ndens 4 + xh_av 8 + phih_grid 16 (RMW)
 CHEM_BYTES_PER_CELL = 44
+DUMP_SAMPLE_CELLS = 1 << 20      # --dump-outputs: cells per grid (8 MB per f64 grid; <= 44 MB in all with --thermal)
 
 
 def _run_reference(exe, mesh, srcpos, normflux, xfield, threads, box_cost):
@@ -247,6 +254,22 @@ def share_leg(pkg, torch, n, share, nd, xh, srcpos, normflux, step, tables, devi
     return out
 
 
+def dump_outputs(d, b, ev, last, thermal):
+    """What the last timed step hands its caller, as d/<name>.npy: the step's scalars (conv_flag and sum_xh1 as Evolve.iteration
+    returns them, the photon loss and sub-box count of the pass), one float64 element each, and the state grids (xh_av,
+    xh_intermed, phih_grid; with --thermal also phiheat_grid and the float32 temperature_grid, ncell x 3) at the same
+    DUMP_SAMPLE_CELLS cells, drawn once from a fixed seed (every cell where the mesh has fewer)."""
+    os.makedirs(d, exist_ok=True)
+    idx = np.arange(b.ncell)
+    if b.ncell > DUMP_SAMPLE_CELLS:
+        idx = np.sort(np.random.default_rng(20261016).choice(b.ncell, DUMP_SAMPLE_CELLS, replace=False))
+    for name in ["xh_av", "xh_intermed", "phih_grid"] + (["phiheat_grid", "temperature_grid"] if thermal else []):
+        np.save(os.path.join(d, name + ".npy"), b.fetch(name)[idx])
+    conv, sum_xh1 = last
+    for name, v in (("conv_flag", conv), ("sum_xh1", sum_xh1), ("photon_loss", ev.photon_loss_all), ("sum_nbox", ev.sum_nbox_all)):
+        np.save(os.path.join(d, name + ".npy"), np.array([v], dtype=np.float64))
+
+
 def self_launch(ngpus):
     """Start `ngpus` ranks of this script under torch.distributed.run as a child process and relay its output."""
     import socket
@@ -286,6 +309,10 @@ def main():
                     help="coarsened cubep3m density file (<z>n_all.dat: 3 x int32 + N^3 float32 stream, nbody_cubep3m.F90:87-107) "
                          "instead of the synthetic field; scaled as scale_density does (density_unit grid, --n-box fine cells per side)")
     ap.add_argument("--n-box", type=int, default=13824, help="fine N-body cells per side of the density file's simulation (nbody_cubep3m.F90:9)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, run the legs that take runs of their own (the --no-* options below skip single ones)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (rank 0; a seeded sample of each grid)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-dropin-leg", action="store_true",
                     help="skip the informational run of the reference driver linked with the Fortran drop-in (128^3, one source, 14 steps)")
@@ -312,6 +339,11 @@ def main():
                     help="time the non-isothermal variant (isothermal=.false.: heating rates in the sweep, thermal.f90 in the "
                          "global pass; synthetic cooling table, T = 1e4 K start).  Not the headline configuration; no CPU baseline")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:       # a plain run: only what the headline needs
+        args.no_cpu_baseline = args.no_dropin_leg = args.no_mix_ceiling = args.no_other_mode = True
+        args.no_small_leg = args.no_configs_leg = True
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without a launcher: this process becomes the launcher.  Nothing here has touched
@@ -447,7 +479,7 @@ def main():
     fused_visited = 0.0        # pairs traced by k_sweep_box_fused (sub-boxes 1 and 2), this rank, timed steps
     nbox_first = None
     for k in range(args.steps):
-        one_step(k)
+        last = one_step(k)
         nbox_hist.append(ev.sum_nbox_all)
         if k == 0 and world == 1:
             nbox_first = b.last_nbox().astype(np.int64)        # per-source sub-box counts of the first timed pass
@@ -462,6 +494,8 @@ def main():
     # checksums of the state the timed steps leave (the same on every rank: Gamma is all-reduced, the global pass replicated)
     check = {"phih_grid_sum": float(b.phih_grid.sum(dtype=torch.float64)), "xh_intermed_sum": float(b.xh_intermed.sum(dtype=torch.float64)),
              "xh_av_sum": float(b.xh_av.sum(dtype=torch.float64)), "sum_nbox_last_step": int(nbox_hist[-1]) if nbox_hist else 0}
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, b, ev, last, args.thermal)
     # max over ranks of the wall time; sum over ranks of the visited pairs
     stats = torch.tensor([dt_wall, float(ev.visited), prof["sweep_ms"], float(prof["sweep_launches"])],
                          dtype=torch.float64, device=b.device)

@@ -9,7 +9,7 @@ OUT=$PWD/gpurun_out/$NAME
 mkdir -p "$OUT"
 export TMPDIR=/tmp
 W=/tmp/prof_$NAME; rm -rf "$W"; mkdir -p "$W"
-python3 bench.py --steps 3 --warmup 1 "$@" > "$OUT/bench.json" 2> "$OUT/bench.err"
+python3 bench.py --steps 3 --warmup 1 --full "$@" > "$OUT/bench.json" 2> "$OUT/bench.err"
 timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$W/kt" -o kt -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-other-mode --no-small-leg --no-configs-leg --no-dropin-leg --no-mix-ceiling "$@" > "$OUT/kt_bench.json" 2> "$OUT/kt.err"
 cp "$(find "$W/kt" -name '*kernel_stats.csv' | head -1)" "$OUT/kernel_stats.csv"
 cp "$(find "$W/kt" -name '*kernel_trace.csv' | head -1)" "$OUT/kernel_trace.csv"

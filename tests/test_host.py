@@ -47,11 +47,11 @@ def test_rccl_binding_exports_its_header(pkg):
     assert "rccl" not in needed
 
 
-def test_struct_layout_matches_header(pkg):
+def test_struct_layout_matches_header(pkg, tmp_path):
     """sizeof() of the two ABI structs as the C compiler sees them."""
     src = ('#include <stdio.h>\n#include "c2ray_hip.h"\nint main(){printf("%zu %zu %zu %zu\\n",sizeof(c2r_params),sizeof(c2r_report),'
            'sizeof(c2r_thermal_params),sizeof(c2r_sed_params));return 0;}\n')
-    exe = "/tmp/c2r_sizeof"
+    exe = str(tmp_path / "c2r_sizeof")
     subprocess.run(["gcc", "-x", "c", "-", "-I", os.path.join(ROOT, "include"), "-o", exe], input=src.encode(), check=True)
     a, b, c, d = map(int, subprocess.check_output([exe]).split())
     import ctypes as C
